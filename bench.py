@@ -14,11 +14,16 @@ reward / done for every step into a device rollout buffer, with the actions read
 (inputs resident before the timed region).  Episode stats are reduced on device and all-reduced
 over RCCL every --stats-every rollouts on a side stream.
 
-Secondary lines (N = 1, after the timed region): the fused policy rollout (config 2), the PPO
-update, MT19937 reset mode, the random-action launch, the numpy (PCIe-inclusive) face, configs
-1 and 4, the single-step face, and the CPU baseline.
+A plain run sets up, pre-warms, runs --warmup steps, times --steps steps in one window (gated;
+host-issued only where the gate cannot be used or did not release), writes the last timed
+launch's outputs if --dump-outputs is given, and prints the line.  Everything else is behind
+--full: the host-issued window beside the gated one (`host_issued`), the gate-release probe, the
+same-box HBM ceiling, the other-scaling line (N > 1) and the secondary lines (N = 1, after the
+timed region): the fused policy rollout (config 2), the PPO update, MT19937 reset mode, the
+random-action launch, the numpy (PCIe-inclusive) face, configs 1 and 4, the single-step face,
+and the CPU baseline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -636,11 +641,48 @@ def stagger_episodes(env, pdist_first: int) -> None:
     env.set_state(px, py, gx, gy, t)
 
 
-def run_config3(args, pkg, rank: int, world: int, dev, total_formations: int, scaling: str):
+def prewarm_regions(prewarm_ms: float, A: int, N: int, D: int, T: int) -> int:
+    """Pre-warm regions (5 launches of T steps each) that fill `prewarm_ms` of device time at a
+    nominal launch time: the launch's algorithmic bytes at 70 % of the HBM spec rate (what the
+    rollout kernel sustains at the headline size), 10 us at the least (small grids are bound by
+    the launch itself).  A function of the arguments alone; at most 20,000."""
+    launch_ms = max(rollout_bytes_per_launch(A, N, D, T) / (0.7 * HBM_PEAK_GBS * 1e9) * 1e3, 0.010)
+    return int(min(20000, max(0.0, -(-prewarm_ms // (5 * launch_ms)))))
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def output_sample(A: int, T: int, D: int):
+    """The agents whose outputs --dump-outputs writes: all of them while a launch's float32 obs /
+    reward / done (and the index itself) fit half of DUMP_BYTES, else a fixed seeded sample (sorted
+    agent indices, the same for every run of the same shape)."""
+    import numpy as np
+    keep = (DUMP_BYTES // 2) // (4 * T * (D + 2) + 8)
+    if A <= keep:
+        return np.arange(A, dtype=np.int64)
+    return np.sort(np.random.default_rng(20240).choice(A, size=keep, replace=False)).astype(np.int64)
+
+
+def write_outputs(dump_dir: str, outputs: dict, idx, suffix: str = "") -> None:
+    """DIR/<name>.npy (float32; episode_stats float64) of the last timed launch's outputs, over
+    the agents of agent_index.npy (output_sample)."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    arrays = {k: v.numpy() for k, v in outputs.items()}
+    arrays["agent_index"] = idx.cpu().numpy().astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES
+    for k, a in arrays.items():
+        np.save(os.path.join(dump_dir, f"{k}{suffix}.npy"), a)
+
+
+def run_config3(args, pkg, rank: int, world: int, dev, total_formations: int, scaling: str,
+                dump_dir=None):
     """One headline measurement (BASELINE config 3 shape) over `total_formations` formations
     sharded contiguously over the ranks; returns the JSON line's fields on rank 0, None
     elsewhere.  Every rank builds its own shard env, buffers and streams; the env is released
-    before returning so a second measurement starts from free HBM."""
+    before returning so a second measurement starts from free HBM.  With `dump_dir`, every rank
+    writes the outputs of the headline window's last launch there (write_outputs)."""
     import torch
     from importlib import import_module
     venv = import_module(pkg.__name__ + ".vectorized_env")
@@ -657,6 +699,7 @@ def run_config3(args, pkg, rank: int, world: int, dev, total_formations: int, sc
     obs = torch.empty((T, A, D), dtype=torch.float32, device=dev)
     rew = torch.empty((T, A), dtype=torch.float32, device=dev)
     done = torch.empty((T, A), dtype=torch.bool, device=dev)
+    dump_idx = (torch.from_numpy(output_sample(A, T, D)).to(dev) if dump_dir else None)
     # Stats pipeline: a stats launch writes its per-wave {reward, done} records into partials[s]
     # on the main stream and records mark[s]; once the NEXT launch has been issued, the side
     # stream waits for mark[s], reduces partials[s] (deterministic order) into reds[s] and
@@ -794,8 +837,8 @@ def run_config3(args, pkg, rank: int, world: int, dev, total_formations: int, sc
     # reduction kernel, the stats reducer's stream); 2) exactly --warmup steps; 3) exactly
     # --steps timed steps.
     # The number of pre-warm regions is agreed over the ranks (each region holds a stats
-    # all-reduce, so every rank must run the same count): one calibration region, then the
-    # max over ranks of the regions still needed.
+    # all-reduce, so every rank must run the same count): the max over ranks of
+    # prewarm_regions(), two of them at the least.
     pw_launches, pw_ms = 0, 0.0
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
@@ -813,11 +856,13 @@ def run_config3(args, pkg, rank: int, world: int, dev, total_formations: int, sc
         gc.collect()
         gc.freeze()
     pw_ms += prewarm_region()      # first use of everything (slow)
-    last = prewarm_region()        # calibration: one warm region
-    pw_ms += last
+    pw_ms += prewarm_region()      # one warm region
     pw_launches += 10
-    more = int(pdist.max_over_ranks(min(20000, max(0.0, -(-(args.prewarm_ms - pw_ms) //
-                                                        max(last, 1e-3)))), dev))
+    # The count comes from the arguments alone, never from this run's timings: the env then
+    # enters the timed steps in the same state on every run of the same command, so two runs
+    # (two builds) compute the same outputs (--dump-outputs).
+    more = int(pdist.max_over_ranks(max(0, prewarm_regions(args.prewarm_ms, A, N, D, T) - 2),
+                                    dev))
     for _ in range(more):
         pw_ms += prewarm_region()
         pw_launches += 5
@@ -916,6 +961,14 @@ def run_config3(args, pkg, rank: int, world: int, dev, total_formations: int, sc
         elapsed = time.perf_counter() - t0
         gc.enable()
         stamp("synchronized")
+        if dump_idx is not None:
+            # what the window's last launch returned (outside the window: after `elapsed`)
+            L = plan[-1]
+            w["outputs"] = {"obs": obs[:L].index_select(1, dump_idx).float().cpu(),
+                            "reward": rew[:L].index_select(1, dump_idx).float().cpu(),
+                            "done": done[:L].index_select(1, dump_idx).float().cpu()}
+            if tot is not None:
+                w["outputs"]["episode_stats"] = tot.double().cpu()
         w.update(elapsed=elapsed, host_issue_ms=t_issued * 1e3, tot=tot,
                  kern_ms=evs[0].elapsed_time(evs[1]), t0=t0,
                  trace=None if trace is None else [(k, round((t - t0) * 1e6, 2))
@@ -931,32 +984,42 @@ def run_config3(args, pkg, rank: int, world: int, dev, total_formations: int, sc
             torch.distributed.barrier()
         return w
 
-    # the host-issued window first (rounds 1-5's measurement), then the gated one (the headline)
-    w_host = window(False)
+    # --full: the host-issued window first (rounds 1-5's measurement), then the gated one (the
+    # headline).  A plain run times the headline window alone: the gated one, and the host-issued
+    # one only where the gate cannot be used or did not release.
+    w_host = window(False) if (args.full or not gated) else None
     w_gate = window(True) if gated else None
-    if not args.no_gc_freeze:
-        gc.unfreeze()
     if w_gate is not None and pdist.max_over_ranks(
             0.0 if w_gate["gate"]["released"] == 1 else 1.0, dev) != 0.0:
         gate_error = f"gate did not release on every rank: {w_gate['gate']}"
         w_gate = None
+    if w_gate is None and w_host is None:
+        w_host = window(False)
+    if not args.no_gc_freeze:
+        gc.unfreeze()
     head = w_gate or w_host
-    gate_probe = gate.probe() if w_gate is not None else None  # after both windows
-    ceiling = hbm_ceiling(acts[0], obs, rew, done, A, T, D, main_s)  # after the timed region
-    # the same byte mix over the first 4 planes only: its 0.17 GB of actions stay in the 256 MB
-    # Infinity Cache from one k_mix launch to the next, so this is NOT an HBM ceiling -- it shows
-    # what the launch's re-read actions cost it (profiles/r5_footprint_ubench.txt)
-    ceiling_small = hbm_ceiling(acts[0], obs, rew, done, A, min(T, 4), D, main_s)
+    if dump_dir:
+        write_outputs(dump_dir, head["outputs"], dump_idx, "" if world == 1 else f"_rank{rank}")
+    ceiling = ceiling_small = gate_probe = None
+    if args.full:
+        gate_probe = gate.probe() if w_gate is not None else None  # after both windows
+        ceiling = hbm_ceiling(acts[0], obs, rew, done, A, T, D, main_s)  # after the timed region
+        # the same byte mix over the first 4 planes only: its 0.17 GB of actions stay in the 256
+        # MB Infinity Cache from one k_mix launch to the next, so this is NOT an HBM ceiling -- it
+        # shows what the launch's re-read actions cost it (DESIGN.md §4.1,
+        # profiles/r5_footprint_ubench.txt)
+        ceiling_small = hbm_ceiling(acts[0], obs, rew, done, A, min(T, 4), D, main_s)
     # per-rank timings of both windows (one all-gather), then the max over ranks
-    wins = [w for w in (w_host, w_gate) if w is not None]
+    named = [(k, w) for k, w in (("host", w_host), ("gated", w_gate)) if w is not None]
+    wins = [w for _, w in named]
     mine = [x for w in wins for x in (w["elapsed"] * 1e3, w["kern_ms"], w["host_issue_ms"],
                                       w.get("start_late_us", 0.0))]
     per = pdist.gather_floats(mine, dev)
-    per_rank = []
-    for i, w in enumerate(wins):
+    per_rank = {}
+    for i, (name, w) in enumerate(named):
         cols = [[r[4 * i + j] for r in per] for j in range(4)]
-        per_rank.append({"elapsed_ms": cols[0], "kernel_ms": cols[1], "host_issue_ms": cols[2],
-                         "start_late_us": cols[3]})
+        per_rank[name] = {"elapsed_ms": cols[0], "kernel_ms": cols[1], "host_issue_ms": cols[2],
+                          "start_late_us": cols[3]}
         w["elapsed_max"] = max(cols[0]) * 1e-3
         w["kern_ms_max"] = max(cols[1])
     elapsed, kern_total_ms, tot = head["elapsed_max"], head["kern_ms_max"], head["tot"]
@@ -998,14 +1061,14 @@ def run_config3(args, pkg, rank: int, world: int, dev, total_formations: int, sc
             "fixed_overhead_ms": elapsed * 1e3 - kern_total_ms,
             "issue": "gated" if head is w_gate else "host",
             **({"gate_error": gate_error} if gate_error else {}),
-            **({"gate": {**head["gate"], "release_probe": gate_probe,
+            **({"gate": {**head["gate"],
+                         **({"release_probe": gate_probe} if gate_probe is not None else {}),
                          "prefix_issue_ms": head["prefix_issue_ms"],
                          "release_clock_ns": head["release_clock_ns"]}}
                if head is w_gate else {}),
-            "host_issued": window_summary(w_host, total_agents, steps),
-            **({"per_rank": {"host": per_rank[0],
-                             **({"gated": per_rank[1]} if w_gate is not None else {})}}
-               if pdist.active() else {}),
+            **({"host_issued": window_summary(w_host, total_agents, steps)}
+               if w_host is not None else {}),
+            **({"per_rank": per_rank} if pdist.active() else {}),
             **({"host_trace_us": head["trace"]} if trace is not None else {}),
             "config": {"workload": workload, "formations": total_formations,
                        "agents_per_formation": N, "obs_dim": D, "rollout_chunk": T,
@@ -1056,6 +1119,33 @@ def run_config3(args, pkg, rank: int, world: int, dev, total_formations: int, sc
     return None, env
 
 
+def secondaries(args, pkg, dev, world: int, N: int, D: int, out: dict) -> None:
+    """--full, N = 1: the secondary lines and the CPU baseline, after the timed region."""
+    if not args.full:
+        return
+    if world == 1 and not args.no_policy:
+        out["policy_rollout"] = secondary(policy_rollout_bench, pkg.__name__, dev, 65536, 10,
+                                          10)
+    if world == 1 and not args.no_policy:
+        out["ppo_update"] = secondary(ppo_update_bench, pkg.__name__, dev)
+    if world == 1 and not args.no_configs:
+        # the PCIe-inclusive numpy face: the reference's default size (config 0) and the
+        # headline size
+        out["numpy_face"] = {
+            "config0": secondary(numpy_face_bench, pkg.__name__, dev, 1000, N, 200),
+            "config3": secondary(numpy_face_bench, pkg.__name__, dev, args.formations, N, 10)}
+        out["mt19937_mode"] = secondary(mt_mode_bench, pkg.__name__, dev, args.formations, N)
+        out["random_action_rollout"] = random_action_bench(pkg.__name__, dev,
+                                                           args.formations, N)
+        out["env_configs"] = {"config1": env_config_bench(pkg.__name__, dev, 4096, 5, 400),
+                              "config4": env_config_bench(pkg.__name__, dev, 16384, 64)}
+        # the single-step face at the headline size: SURVEY §8(d)'s B_step per agent-step
+        out["single_step"] = env_config_bench(pkg.__name__, dev, args.formations, N, 500,
+                                              T=1)
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(N, D, args.cpu_baseline_seconds)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1080,7 +1170,9 @@ def main():
     ap.add_argument("--no-goal", action="store_true")
     ap.add_argument("--prewarm-ms", type=float, default=400.0,
                     help="device-time pre-warm (clocks, first-touch of the buffers) before the "
-                         "--warmup steps; independent of --warmup, reported as warmup_ms")
+                         "--warmup steps, as a launch count fixed by the arguments "
+                         "(prewarm_regions); independent of --warmup, its measured time reported "
+                         "as warmup_ms")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--issue", default="gated", choices=["gated", "host"],
@@ -1098,6 +1190,15 @@ def main():
     ap.add_argument("--no-policy", action="store_true", help="skip the config-2 policy rollout")
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the secondary env-only lines (BASELINE configs[1] and [4])")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline window: the host-issued "
+                         "window, the gate probe, the same-box HBM ceiling, the other-scaling line "
+                         "(N > 1), the secondary lines and the CPU baseline (N = 1; the --no-* "
+                         "switches above pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed launch returned (obs, "
+                         "reward, done of a fixed seeded sample of the agents, and the episode "
+                         "stats) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0 or args.chunk < 1:
         ap.error("need --steps >= 1, --warmup >= 0, --chunk >= 1")
@@ -1125,7 +1226,8 @@ def main():
     # BASELINE config 3 as written: 1,048,576 formations sharded over the GPUs (strong); the
     # weak line (1,048,576 formations on every GPU) rides along as a nested measurement
     total = args.formations if scaling == "strong" else args.formations * world
-    out, env = run_config3(args, pkg, rank, world, dev, total, scaling)
+    out, env = run_config3(args, pkg, rank, world, dev, total, scaling,
+                           dump_dir=args.dump_outputs)
     if rank == 0:
         # the collectives of the line (stats all-reduce, barriers, max over ranks): "none" when no
         # process group is up (the driver's N = 1 run); FENV_DIST_FORCE=1 runs them at world 1
@@ -1133,7 +1235,7 @@ def main():
                        "world": world}
     env.release()
     del env
-    if world > 1 and not args.no_weak_line:
+    if args.full and world > 1 and not args.no_weak_line:
         other = "weak" if scaling == "strong" else "strong"
         tot2 = args.formations * world if other == "weak" else args.formations
         o2, env2 = run_config3(args, pkg, rank, world, dev, tot2, other)
@@ -1145,27 +1247,7 @@ def main():
                     "host_issued", "per_rank")
             out[f"{other}_scaling_line"] = {k: o2[k] for k in keep if k in o2}
     if rank == 0:
-        if world == 1 and not args.no_policy:
-            out["policy_rollout"] = secondary(policy_rollout_bench, pkg.__name__, dev, 65536, 10,
-                                              10)
-        if world == 1 and not args.no_policy:
-            out["ppo_update"] = secondary(ppo_update_bench, pkg.__name__, dev)
-        if world == 1 and not args.no_configs:
-            # the PCIe-inclusive numpy face: the reference's default size (config 0) and the
-            # headline size
-            out["numpy_face"] = {
-                "config0": secondary(numpy_face_bench, pkg.__name__, dev, 1000, N, 200),
-                "config3": secondary(numpy_face_bench, pkg.__name__, dev, args.formations, N, 10)}
-            out["mt19937_mode"] = secondary(mt_mode_bench, pkg.__name__, dev, args.formations, N)
-            out["random_action_rollout"] = random_action_bench(pkg.__name__, dev,
-                                                               args.formations, N)
-            out["env_configs"] = {"config1": env_config_bench(pkg.__name__, dev, 4096, 5, 400),
-                                  "config4": env_config_bench(pkg.__name__, dev, 16384, 64)}
-            # the single-step face at the headline size: SURVEY §8(d)'s B_step per agent-step
-            out["single_step"] = env_config_bench(pkg.__name__, dev, args.formations, N, 500,
-                                                  T=1)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(N, D, args.cpu_baseline_seconds)
+        secondaries(args, pkg, dev, world, N, D, out)
         print(json.dumps(out), flush=True)
     if pdist.active():
         torch.distributed.destroy_process_group()

@@ -51,3 +51,37 @@ def test_gate_prefix_and_alignment_constants():
     assert bench.GATE_PREFIX >= 2          # the driver's --steps 20 window is gated whole
     assert 0 < bench.ALIGN_MARGIN_NS <= 5_000_000
     assert bench._Gate.TIMEOUT_US <= 60_000_000   # fenv_stream_gate's limit
+
+
+def test_output_sample_is_fixed_and_within_the_dump_limit(tmp_path):
+    """--dump-outputs: every agent while a launch's outputs fit, else the same sorted sample of
+    distinct agents on every call; what write_outputs stores stays within DUMP_BYTES."""
+    import numpy as np
+    import torch
+    assert bench.DUMP_BYTES == 64 << 20
+    assert np.array_equal(bench.output_sample(1000, 10, 8), np.arange(1000))
+    A, T, D = 5_242_880, 10, 8  # the headline shape
+    idx = bench.output_sample(A, T, D)
+    assert np.array_equal(idx, bench.output_sample(A, T, D))
+    assert idx.dtype == np.int64 and 0 <= idx[0] and idx[-1] < A and (np.diff(idx) > 0).all()
+    assert len(idx) * (4 * T * (D + 2) + 8) <= bench.DUMP_BYTES
+    n = 7
+    outs = {"obs": torch.zeros((T, n, D)), "reward": torch.ones((T, n)),
+            "done": torch.zeros((T, n)), "episode_stats": torch.zeros(2, dtype=torch.float64)}
+    bench.write_outputs(str(tmp_path / "d"), outs, torch.from_numpy(idx[:n]))
+    got = {p.stem: np.load(p) for p in (tmp_path / "d").glob("*.npy")}
+    assert set(got) == set(outs) | {"agent_index"}
+    assert got["obs"].dtype == np.float32 and got["episode_stats"].dtype == np.float64
+    assert np.array_equal(got["agent_index"], idx[:n]) and got["reward"].sum() == T * n
+
+
+def test_prewarm_count_depends_on_the_arguments_alone():
+    """The pre-warm's launch count is a function of the arguments (no timing), so the env enters
+    the timed steps in the same state on every run: 400 ms at the headline shape is 182 regions
+    of five 0.44-ms launches (2.46 GB at 5.6 TB/s), none for --prewarm-ms 0, and a launch never
+    counts as shorter than 10 us."""
+    A = 5_242_880
+    assert bench.prewarm_regions(400.0, A, 5, 8, 10) == 182
+    assert bench.prewarm_regions(0.0, A, 5, 8, 10) == 0
+    assert bench.prewarm_regions(400.0, 5, 5, 8, 10) == 8000
+    assert bench.prewarm_regions(1e9, A, 5, 8, 10) == 20000

@@ -14,9 +14,10 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the 8-way shard size of config 3; --prewarm-ms 0: a fixed pre-warm (2 regions), so both runs
-# step the env through the same launches
+# step the env through the same launches; --full: the host-issued window beside the gated one
+# and the gate probe (its secondary lines are switched off one by one)
 ARGS = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--formations", "131072",
-        "--prewarm-ms", "0", "--no-policy", "--no-configs", "--no-cpu-baseline"]
+        "--prewarm-ms", "0", "--full", "--no-policy", "--no-configs", "--no-cpu-baseline"]
 
 
 def _port():
@@ -27,12 +28,12 @@ def _port():
     return p
 
 
-def _bench(env_extra):
+def _bench(env_extra, args=ARGS):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "FENV_DIST_FORCE", "FENV_DIST_BACKEND"):
         env.pop(k, None)
     env.update(env_extra)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + ARGS, cwd=ROOT, env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -70,6 +71,39 @@ def test_bench_falls_back_to_host_window_when_gate_times_out():
     d = _bench({"FENV_BENCH_GATE_TEST": "no-release"})
     assert d["issue"] == "host" and "did not release" in d["gate_error"]
     assert d["value"] == d["host_issued"]["value"] and "gate" not in d
+
+
+def test_plain_run_times_one_window_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the headline window alone (no host-issued window, probe,
+    ceiling or secondary line), and --dump-outputs writes the last timed launch's obs / reward /
+    done (here every agent: 4,099 x 5 fit the size limit) and the episode stats.  One 10-step
+    launch, so the stats launch is the dumped one: its done count equals the dumped flags' sum
+    exactly, its reward sum the dumped rewards' (fp32 per-wave partial sums of <= 640 terms, then
+    double: 640 x 2^-24 < 1e-4 of the sum of magnitudes)."""
+    import numpy as np
+    F, N, T = 4099, 5, 10
+    d = _bench({}, ["--gpus", "1", "--steps", str(T), "--warmup", "5", "--formations", str(F),
+                    "--prewarm-ms", "0", "--dump-outputs", str(tmp_path)])
+    assert d["issue"] == "gated" and d["gate"]["released"] == 1 and d["steps"] == T
+    assert d["ms_per_step"] > 0  # one timed step's wall time: value = agents / that
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - F * N) < 1e-6 * F * N
+    for k in ("host_issued", "policy_rollout", "ppo_update", "numpy_face", "mt19937_mode",
+              "random_action_rollout", "env_configs", "single_step", "cpu_baseline"):
+        assert k not in d, k
+    assert "release_probe" not in d["gate"] and "same_box_ceiling" not in d["roofline"]
+    out = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(out) == {"obs", "reward", "done", "episode_stats", "agent_index"}
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert np.array_equal(out["agent_index"], np.arange(F * N))
+    assert out["obs"].shape == (T, F * N, 8) and np.isfinite(out["obs"]).all()
+    assert out["reward"].shape == out["done"].shape == (T, F * N)
+    assert set(np.unique(out["done"])) <= {0.0, 1.0}
+    rsum, dones = out["episode_stats"]
+    assert dones == out["done"].sum(dtype=np.float64)
+    assert dones == d["episode_stats"]["agent_dones_sampled_rollout"]
+    rew64 = out["reward"].astype(np.float64)
+    assert abs(rsum - rew64.sum()) <= 1e-4 * np.abs(rew64).sum()
 
 
 def test_ppo_collectives_over_rccl_world1():

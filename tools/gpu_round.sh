@@ -19,10 +19,10 @@ fi
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke: ok')" > "$O/smoke.log" 2>&1 \
   || fatal $? smoke
 echo "smoke ok"
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" || fatal $? bench_driver
+timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/bench_driver.json" 2> "$O/bench_driver.err" || fatal $? bench_driver
 echo "bench(driver cmd):"; cat "$O/bench_driver.json" | cut -c1-900
 if [ -z "${SKIP_DEFAULT:-}" ]; then
-  timeout -k 10 300 python bench.py > "$O/bench_default.json" 2> "$O/bench_default.err" || fatal $? bench_default
+  timeout -k 10 300 python bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err" || fatal $? bench_default
   echo "bench(default) done"
 fi
 cd /tmp && export TMPDIR=/tmp
@@ -37,6 +37,6 @@ python3 "$R/tools/pmc_summary.py" "$R/gpurun_out" "$TAG" > "$O/pmc_summary.txt" 
 # profiled process made a cooperative launch (the PPO update's split launch; DESIGN §9.4,
 # profiles/r4_rocprof_coop_exit/), so nothing may follow it in this call.
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_driver" -o bench \
-  -- python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver_under_rocprof.json" 2> "$O/prof_driver.err" \
+  -- python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --full > "$O/bench_driver_under_rocprof.json" 2> "$O/prof_driver.err" \
   || fatal $? rocprof
 echo "rocprof ok"

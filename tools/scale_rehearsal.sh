@@ -12,7 +12,7 @@ mkdir -p "$O"
 export PYTHONUNBUFFERED=1
 for F in ${SIZES:-131072 262144 524288 1048576}; do
   for rep in $(seq 1 ${REPS:-3}); do
-    timeout -k 10 120 python bench.py --gpus 1 --steps 20 --warmup 5 --formations $F --no-policy \
+    timeout -k 10 120 python bench.py --gpus 1 --steps 20 --warmup 5 --formations $F --full --no-policy \
       --no-configs --no-cpu-baseline > "$O/shard_${F}_$rep.json" 2> "$O/shard_${F}_$rep.err" || exit $?
   done
 done
@@ -34,7 +34,7 @@ for F, v in sorted(rows.items()):
 PY
 if [ -z "${SKIP_GLOO:-}" ]; then
   FENV_DIST_BACKEND=gloo timeout -k 10 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 \
+    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 --full \
     --formations 262144 > "$O/rehearse_2rank.json" 2> "$O/rehearse_2rank.err"
   rc=$?; echo "2-rank rc=$rc"; cut -c1-400 "$O/rehearse_2rank.json"; exit $rc
 fi
