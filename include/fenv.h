@@ -38,8 +38,10 @@ extern "C" {
  *   3  + fenv_status, fenv_test_stage_hook, fenv_pinned_pool_bytes, fenv_debug_staging (no
  *        signature changed)
  *   4  + fenv_host_alloc, fenv_host_free (no signature changed)
- *   5  + fenv_stream_gate (no signature changed) */
-#define FENV_ABI_VERSION 5
+ *   5  + fenv_stream_gate (no signature changed)
+ *   6  + fenv_control, fenv_rollout_velocity, fenv_rollout_control, fenv_control_neighbor_dist
+ *        (no signature changed) */
+#define FENV_ABI_VERSION 6
 int fenv_abi_version(void);
 
 typedef struct fenv fenv_t;
@@ -160,6 +162,42 @@ int fenv_rollout(fenv_t *env, int32_t T, const float *act, float *obs, float *re
 int fenv_rollout_random(fenv_t *env, int32_t T, uint64_t act_seed, uint64_t step_offset,
                         float *act_out, float *obs, float *rew, uint8_t *done, float *partial,
                         void *stream);
+
+/* ------------------------------------------------------------------ baseline controller
+ * The reference's potential-field formation controller control(i, env) (simulate.py:256-319, run
+ * by `python simulate.py`, :321-329): the baseline the RL policy is compared with.  It steps a
+ * FormationSimulator with a raw velocity (simulate.py:70 step(input_velocity)); the x10 action
+ * scaling belongs to FormationEnv.step one layer up (vectorized_env.py:69-70), and
+ * 10 * (v / 10) is not v in fp32, so fenv_step / fenv_rollout cannot carry a controller's
+ * velocity bit-exactly: the velocity entry points below can.  All three take formations of at
+ * most 1,024 agents (FENV_EINVAL above: the large-formation path has no controller kernels).
+ *
+ * fenv_control: the velocity control() hands to env.step for every agent of the current state,
+ * vel [A][2] (simulate.py:262-319 in the reference's fp32 operation order: spring terms towards
+ * the next, previous and opposite agents with rest lengths pi * 40 / N, pi * 40 / N and 80,
+ * clipped to [-1, 1] per component, plus the clipped goal attraction; coincident agents give
+ * NaN as in the reference).  The state is not changed.  num_agents must be even
+ * (simulate.py:279 asserts it): FENV_EINVAL otherwise. */
+int fenv_control(fenv_t *env, float *vel, void *stream);
+
+/* FormationSimulator.step(input_velocity) (simulate.py:70-118) of every formation, T times in
+ * one launch: vel [T][A][2] is added to the positions unscaled (simulate.py:82).  Everything else
+ * -- obs / rew / done layouts, NULL outputs, the partial records and fenv_partial_count, the
+ * split at MT19937 reset events -- is fenv_rollout's.  Any 1 <= num_agents <= 1024. */
+int fenv_rollout_velocity(fenv_t *env, int32_t T, const float *vel, float *obs, float *rew,
+                          uint8_t *done, float *partial, void *stream);
+
+/* T steps of control(i, env) for every formation fused in one launch (the reference's animation
+ * loop, simulate.py:324-328): per step the controller's velocities are computed from the state
+ * held on chip and applied as fenv_rollout_velocity applies them.  vel_out (may be NULL)
+ * receives them, [T][A][2].  Bit-identical to T x (fenv_control + fenv_rollout_velocity(T = 1)).
+ * num_agents must be even. */
+int fenv_rollout_control(fenv_t *env, int32_t T, float *vel_out, float *obs, float *rew,
+                         uint8_t *done, float *partial, void *stream);
+
+/* Host-only: the controller's fp32 desired neighbour distance, pi * desired_radius / num_agents
+ * with desired_radius = 40 (simulate.py:259, :286; not the reward's radius of 60, :25). */
+float fenv_control_neighbor_dist(int32_t num_agents);
 
 /* Number of float2 partial records fenv_rollout writes (see fenv_rollout; independent of T). */
 int64_t fenv_partial_count(const fenv_t *env);

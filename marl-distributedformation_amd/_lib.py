@@ -42,6 +42,10 @@ SIGNATURES = {
     "fenv_step": (_I32, [_P, _P, _P, _P, _P, _P]),
     "fenv_rollout": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P]),
     "fenv_rollout_random": (_I32, [_P, _I32, _U64, _U64, _P, _P, _P, _P, _P, _P]),
+    "fenv_control": (_I32, [_P, _P, _P]),
+    "fenv_rollout_velocity": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P]),
+    "fenv_rollout_control": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P]),
+    "fenv_control_neighbor_dist": (ctypes.c_float, [_I32]),
     "fenv_partial_count": (_I64, [_P]),
     "fenv_rollout_kernel": (ctypes.c_char_p, [_P, _I32]),
     "fenv_reduce_partials": (_I32, [_P, _I64, _P, _P]),

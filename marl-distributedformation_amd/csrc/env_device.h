@@ -117,10 +117,12 @@ __device__ __forceinline__ void draw_reset(const Consts &c, const DevPending &p,
 
 // ---------------------------------------------------------------- ring-neighbour exchange
 // Three exchange rounds per env step: A {px,py}->prev,next, C {ind}->prev,next, D {nx,ny}->
-// prev,next (round 1 had four: A {px,py}->next, B {drr}->prev, C, D).
+// prev,next (round 1 had four: A {px,py}->next, B {drr}->prev, C, D).  The formation controller
+// (control_kernels.hip) adds one of its own ahead of them: Q {px,py}->prev,next,opposite.
 
 struct WaveX {  // N <= 64: lanes of one formation are contiguous in the wavefront
     int lp, ln;
+    int lo;  // lane of the agent N/2 further round the ring (q_pno only; N even)
     __device__ __forceinline__ void a_next(float u, float v, float &un, float &vn) const {
         un = __shfl(u, ln, 64);
         vn = __shfl(v, ln, 64);
@@ -143,16 +145,27 @@ struct WaveX {  // N <= 64: lanes of one formation are contiguous in the wavefro
         vp = __shfl(v, lp, 64);
         vn = __shfl(v, ln, 64);
     }
+    __device__ __forceinline__ void q_pno(float u, float v, float &up, float &un, float &uo,
+                                          float &vp, float &vn, float &vo) const {
+        up = __shfl(u, lp, 64);
+        un = __shfl(u, ln, 64);
+        uo = __shfl(u, lo, 64);
+        vp = __shfl(v, lp, 64);
+        vn = __shfl(v, ln, 64);
+        vo = __shfl(v, lo, 64);
+    }
 };
 
 constexpr int kMaxN = 1024;
 
 // N > 64: one formation per workgroup, slots in LDS.  Each slot's next write is separated from
-// its previous reads by at least one barrier (rounds are used in the order A,[B,]C,D; A and a_pn
-// share slots 0-1).
+// its previous reads by at least one barrier (rounds are used in the order [Q,]A,[B,]C,[D]; A and
+// a_pn share slots 0-1; Q has slots 2 and 6 to itself -- D may be skipped, so it can share
+// neither C's nor D's -- and the barriers of A and C lie between its reads and its next writes).
 struct BlockX {
-    float *lds;  // 6 * kMaxN floats
+    float *lds;  // 6 * kMaxN floats (7 * kMaxN where q_pno is used)
     int i, ip, in;
+    int io;  // index of the agent N/2 further round the ring (q_pno only; N even)
     __device__ __forceinline__ void a_next(float u, float v, float &un, float &vn) const {
         lds[0 * kMaxN + i] = u;
         lds[1 * kMaxN + i] = v;
@@ -186,6 +199,20 @@ struct BlockX {
         vp = lds[5 * kMaxN + ip];
         vn = lds[5 * kMaxN + in];
     }
+    // the opposite agent's position comes from the slots the prev/next exchange filled, after
+    // the same barrier
+    __device__ __forceinline__ void q_pno(float u, float v, float &up, float &un, float &uo,
+                                          float &vp, float &vn, float &vo) const {
+        lds[2 * kMaxN + i] = u;
+        lds[6 * kMaxN + i] = v;
+        __syncthreads();
+        up = lds[2 * kMaxN + ip];
+        un = lds[2 * kMaxN + in];
+        uo = lds[2 * kMaxN + io];
+        vp = lds[6 * kMaxN + ip];
+        vn = lds[6 * kMaxN + in];
+        vo = lds[6 * kMaxN + io];
+    }
 };
 
 // ---------------------------------------------------------------- one env step of one agent
@@ -205,13 +232,16 @@ struct Agent {
 // (f, a) index a formation that is not its own, or none (the round-2/3
 // post-reset failures were these lanes' terminal-state stores of zeros, past the end of the
 // terminal buffer into the staged reset set that follows it in memory).
+// env_step_v takes the step's velocity (simulate.py:70 input_velocity); env_step, below, the
+// action of the SB3 face.
 template <int MODE, class X, bool TERM = true>
-__device__ __forceinline__ void env_step(const Consts &c, const DevPending &p, const X &x,
-                                         int64_t f, int64_t a, int i, bool live, float2 act,
-                                         Agent &s, float &rw, bool &dn, bool &did_reset) {
-    // vectorized_env.py:69-70 (v = 10 * a), simulate.py:82 (agents += v)
-    const float x1 = s.px + 10.0f * act.x;
-    const float y1 = s.py + 10.0f * act.y;
+__device__ __forceinline__ void env_step_v(const Consts &c, const DevPending &p, const X &x,
+                                           int64_t f, int64_t a, int i, bool live, float vx,
+                                           float vy, Agent &s, float &rw, bool &dn,
+                                           bool &did_reset) {
+    // simulate.py:82 (agents += v)
+    const float x1 = s.px + vx;
+    const float y1 = s.py + vy;
     // simulate.py:86-87: out of bounds tested on the unclipped position
     const bool oob = (x1 <= 0.0f) | (y1 <= 0.0f) | (x1 >= kW) | (y1 >= kH);
     s.px = clip0(x1, kW);
@@ -254,6 +284,15 @@ __device__ __forceinline__ void env_step(const Consts &c, const DevPending &p, c
         s.ep = ep_new;
         did_reset = true;
     }
+}
+
+// FormationEnv.step's face of it: vectorized_env.py:69-70 (v = 10 * a), then the simulator step.
+template <int MODE, class X, bool TERM = true>
+__device__ __forceinline__ void env_step(const Consts &c, const DevPending &p, const X &x,
+                                         int64_t f, int64_t a, int i, bool live, float2 act,
+                                         Agent &s, float &rw, bool &dn, bool &did_reset) {
+    env_step_v<MODE, X, TERM>(c, p, x, f, a, i, live, 10.0f * act.x, 10.0f * act.y, s, rw, dn,
+                              did_reset);
 }
 
 // compute_obs (simulate.py:150-174) of this lane's agent into o[0..D).

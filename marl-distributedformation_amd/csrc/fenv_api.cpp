@@ -812,14 +812,15 @@ int fenv_observe(fenv_t *e, float *obs, void *stream) {
     return FENV_OK;
 }
 
-// fenv_rollout / fenv_rollout_random: T fused steps, split at MT19937 reset events.  gen = NULL:
-// actions from `act`; else generated in the kernel (gen->offset / gen->out advance per launch).
-static int rollout_impl(fenv_t *e, int32_t T, const float *act, const fenvk::ActGen *gen,
-                        float *obs, float *rew, uint8_t *done, float *partial, void *stream) {
+// T fused steps of any rollout entry point, split into launches at MT19937 reset events (and by
+// rollout_launch_steps).  launch(consts, k0, L, accumulate, nt, st) queues the launch of local
+// steps [k0, k0 + L) with the constants `consts` and returns its hipError_t.
+extern "C++" {  // a template inside the ABI's extern "C" block
+template <class Launch>
+static int rollout_split(fenv_t *e, int32_t T, void *stream, Launch &&launch) {
     if (int rc = e->stage_check()) return rc;
     FENV_HIP(hipSetDevice(e->device));
     hipStream_t st = as_stream(stream);
-    const int64_t A = e->A, D = e->D;
     int64_t k0 = 0;
     if (T > 0) {
         int rc = e->wait_pending(st);
@@ -841,16 +842,7 @@ static int rollout_impl(fenv_t *e, int32_t T, const float *act, const fenvk::Act
                 event = true;
             }
         }
-        fenvk::ActGen g{};
-        if (gen) {
-            g = *gen;
-            g.offset += (uint64_t)k0;
-            if (g.out) g.out += k0 * A * 2;
-        }
-        FENV_HIP(fenvk::launch_rollout(
-            e->launch_consts(event), e->s, e->pending(), (int32_t)L, (int32_t)D, act ? act + k0 * A * 2 : nullptr,
-            obs ? obs + k0 * A * D : nullptr, rew ? rew + k0 * A : nullptr,
-            done ? done + k0 * A : nullptr, partial, k0 > 0, nt, st, gen ? &g : nullptr));
+        FENV_HIP(launch(e->launch_consts(event), k0, (int32_t)L, k0 > 0, nt, st));
         e->advance_t(L);
         if (event) {
             int rc = e->gen_pending(st);
@@ -863,6 +855,90 @@ static int rollout_impl(fenv_t *e, int32_t T, const float *act, const fenvk::Act
         k0 += L;
     }
     return FENV_OK;
+}
+}  // extern "C++"
+
+// fenv_rollout / fenv_rollout_random.  gen = NULL: actions from `act`; else generated in the
+// kernel (gen->offset / gen->out advance per launch).
+static int rollout_impl(fenv_t *e, int32_t T, const float *act, const fenvk::ActGen *gen,
+                        float *obs, float *rew, uint8_t *done, float *partial, void *stream) {
+    const int64_t A = e->A, D = e->D;
+    return rollout_split(e, T, stream, [&](const fenvk::Consts &c, int64_t k0, int32_t L,
+                                           bool accum, bool nt, hipStream_t st) {
+        fenvk::ActGen g{};
+        if (gen) {
+            g = *gen;
+            g.offset += (uint64_t)k0;
+            if (g.out) g.out += k0 * A * 2;
+        }
+        return fenvk::launch_rollout(c, e->s, e->pending(), L, (int32_t)D,
+                                     act ? act + k0 * A * 2 : nullptr,
+                                     obs ? obs + k0 * A * D : nullptr,
+                                     rew ? rew + k0 * A : nullptr, done ? done + k0 * A : nullptr,
+                                     partial, accum, nt, st, gen ? &g : nullptr);
+    });
+}
+
+// fenv_rollout_control / fenv_rollout_velocity: the controller's kernels (control_kernels.hip),
+// velocities computed in the kernel (`computed`; vel_out optional) or read from vel_in.
+static int control_rollout_impl(fenv_t *e, int32_t T, bool computed, const float *vel_in,
+                                float *vel_out, float *obs, float *rew, uint8_t *done,
+                                float *partial, void *stream) {
+    const int64_t A = e->A, D = e->D;
+    const float dd = fenv_control_neighbor_dist(e->c.N);
+    return rollout_split(e, T, stream, [&](const fenvk::Consts &c, int64_t k0, int32_t L,
+                                           bool accum, bool, hipStream_t st) {
+        return fenvk::launch_control_rollout(
+            c, e->s, e->pending(), L, (int32_t)D, dd, computed,
+            vel_in ? vel_in + k0 * A * 2 : nullptr, vel_out ? vel_out + k0 * A * 2 : nullptr,
+            obs ? obs + k0 * A * D : nullptr, rew ? rew + k0 * A : nullptr,
+            done ? done + k0 * A : nullptr, partial, accum, st);
+    });
+}
+
+// The controller's entry points cover formations up to one workgroup.
+static int control_size_check(const fenv_t *e, const char *what, bool need_even) {
+    if (fenvk::large_path(e->c.N))
+        return fail(FENV_EINVAL, std::string(what) + ": formations above 1024 agents are not "
+                                 "supported by the controller / velocity entry points");
+    if (need_even && (e->c.N & 1))
+        return fail(FENV_EINVAL, std::string(what) + ": the formation controller needs an even "
+                                 "num_agents (simulate.py:279 asserts num_agents % 2 == 0)");
+    return FENV_OK;
+}
+
+float fenv_control_neighbor_dist(int32_t num_agents) {
+    // simulate.py:286 with desired_radius = 40 (:259) in float64 (numpy), rounded to fp32 where
+    // it meets the fp32 tensor (:290-291).
+    return (float)(M_PI * 40 / (double)num_agents);
+}
+
+int fenv_control(fenv_t *e, float *vel, void *stream) {
+    if (!e) return fail(FENV_EINVAL, "fenv_control: NULL handle");
+    if (!vel) return fail(FENV_EINVAL, "fenv_control: vel is NULL");
+    if (int rc = control_size_check(e, "fenv_control", true)) return rc;
+    if (int rc = e->stage_check()) return rc;
+    FENV_HIP(hipSetDevice(e->device));
+    FENV_HIP(fenvk::launch_control(e->c, e->s, fenv_control_neighbor_dist(e->c.N), vel,
+                                   as_stream(stream)));
+    return FENV_OK;
+}
+
+int fenv_rollout_velocity(fenv_t *e, int32_t T, const float *vel, float *obs, float *rew,
+                          uint8_t *done, float *partial, void *stream) {
+    if (!e) return fail(FENV_EINVAL, "fenv_rollout_velocity: NULL handle");
+    if (T < 0) return fail(FENV_EINVAL, "fenv_rollout_velocity: T must be >= 0");
+    if (!vel && T > 0) return fail(FENV_EINVAL, "fenv_rollout_velocity: vel is NULL");
+    if (int rc = control_size_check(e, "fenv_rollout_velocity", false)) return rc;
+    return control_rollout_impl(e, T, false, vel, nullptr, obs, rew, done, partial, stream);
+}
+
+int fenv_rollout_control(fenv_t *e, int32_t T, float *vel_out, float *obs, float *rew,
+                         uint8_t *done, float *partial, void *stream) {
+    if (!e) return fail(FENV_EINVAL, "fenv_rollout_control: NULL handle");
+    if (T < 0) return fail(FENV_EINVAL, "fenv_rollout_control: T must be >= 0");
+    if (int rc = control_size_check(e, "fenv_rollout_control", true)) return rc;
+    return control_rollout_impl(e, T, true, nullptr, vel_out, obs, rew, done, partial, stream);
 }
 
 int fenv_rollout(fenv_t *e, int32_t T, const float *act, float *obs, float *rew, uint8_t *done,

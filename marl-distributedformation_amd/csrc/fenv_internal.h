@@ -1,5 +1,5 @@
 // Internal interface between the C-ABI host layer (fenv_api.cpp) and the gfx950 kernels
-// (fenv_kernels.hip, policy_kernels.hip).  Not installed; the public ABI is include/fenv.h.
+// (fenv_kernels.hip, control_kernels.hip, policy_kernels.hip).  Not installed; the public ABI is include/fenv.h.
 #pragma once
 
 #include <hip/hip_runtime.h>  // __host__ __device__ for the staged-set tag helpers
@@ -110,6 +110,16 @@ hipError_t launch_rollout(const Consts &c, const DevState &s, const DevPending &
                           int32_t D, const float *act, float *obs, float *rew, uint8_t *done,
                           float *partial, bool accumulate, bool nt, hipStream_t st,
                           const ActGen *gen = nullptr);
+// Baseline formation controller (control_kernels.hip; N <= kBlockMaxN only).  launch_control:
+// the controller's velocities [A][2] of the current state.  launch_control_rollout: T fused steps
+// whose velocities are computed by the controller (`computed`; vel_out optional) or read from
+// vel_in [T][A][2]; outputs and partial records as launch_rollout.  dd: control_neighbor_dist(N).
+hipError_t launch_control(const Consts &c, const DevState &s, float dd, float *vel,
+                          hipStream_t st);
+hipError_t launch_control_rollout(const Consts &c, const DevState &s, const DevPending &p,
+                                  int32_t T, int32_t D, float dd, bool computed,
+                                  const float *vel_in, float *vel_out, float *obs, float *rew,
+                                  uint8_t *done, float *partial, bool accumulate, hipStream_t st);
 hipError_t launch_reset_observe(const Consts &c, const DevState &s, const DevPending &p,
                                 int32_t D, bool do_reset, float *obs, hipStream_t st);
 // kMetricCols columns per formation (include/fenv.h fenv_metrics); `terminal`: formations with

@@ -16,7 +16,9 @@ reference                  here
 =========================  ===================================================================
 
 Device faces (no PCIe per step): :meth:`step_tensor`, :meth:`rollout`, :meth:`observe_tensor`,
-:meth:`metrics`, :meth:`get_state` / :meth:`set_state`.
+:meth:`metrics`, :meth:`get_state` / :meth:`set_state`; the baseline controller and the simulator's
+velocity step (simulate.py:70, :256-319): :meth:`control_tensor`, :meth:`rollout_control`,
+:meth:`rollout_velocity`, :meth:`step_velocity_tensor`, :meth:`step_velocity` (baseline.py).
 
 Parity: with ``reset_mode="mt19937"`` (default) and ``seed=s`` the env reproduces, bit for bit,
 the reference constructed right after ``torch.manual_seed(s)`` (tests/test_gpu_parity.py).
@@ -434,6 +436,106 @@ class FormationEnv(_BASE):
             self._h, T, int(act_seed) & 0xFFFFFFFFFFFFFFFF, int(step_offset) & 0xFFFFFFFFFFFFFFFF,
             _lib.ptr(act_out), _lib.ptr(obs), _lib.ptr(rew), _lib.ptr(done), _lib.ptr(partial),
             self._stream()), "fenv_rollout_random")
+        return obs, rew, done
+
+    # ------------------------------------------------------------------ baseline controller
+    def _check_vel(self, vel, lead: tuple) -> torch.Tensor:
+        if not isinstance(vel, torch.Tensor):
+            raise TypeError(f"velocities must be a float32 tensor on {self.device}")
+        shape = lead + (self.num_envs, 2)
+        if vel.shape != shape:  # simulate.py:79 asserts input_velocity.shape == agents.shape
+            raise AssertionError(f"velocities shape {tuple(vel.shape)} != {shape}")
+        if vel.dtype != torch.float32 or not self._on_device(vel):
+            raise TypeError(f"velocities must be float32 on {self.device}")
+        return vel.contiguous()
+
+    def _rollout_outputs(self, T: int, obs, rew, done, partial):
+        A, D, dev = self.num_envs, self.obs_dim, self.device
+        if obs is None:
+            obs = torch.empty((T, A, D), dtype=torch.float32, device=dev)
+        if rew is None:
+            rew = torch.empty((T, A), dtype=torch.float32, device=dev)
+        if done is None:
+            done = torch.empty((T, A), dtype=torch.bool, device=dev)
+        self._check_out("obs", obs, (T, A, D), torch.float32)
+        self._check_out("rew", rew, (T, A), torch.float32)
+        self._check_out("done", done, (T, A), torch.bool)
+        self._check_partial(partial)
+        return obs, rew, done
+
+    def control_tensor(self, out=None) -> torch.Tensor:
+        """The baseline controller's velocities for the current state (``fenv_control``, the
+        reference's ``control(i, env)`` of simulate.py:256-319 for every formation, up to its
+        ``env.step`` call): device tensor [A, 2].  The state is not changed.  Needs an even
+        ``num_agents_per_formation`` of at most 1,024."""
+        if out is None:
+            out = torch.empty((self.num_envs, 2), dtype=torch.float32, device=self.device)
+        self._check_out("out", out, (self.num_envs, 2), torch.float32)
+        _lib.check(_lib.lib().fenv_control(self._h, _lib.ptr(out), self._stream()),
+                   "fenv_control")
+        return out
+
+    def rollout_velocity(self, vel: torch.Tensor, obs=None, rew=None, done=None, partial=None):
+        """T fused simulator steps with raw velocities (``fenv_rollout_velocity``;
+        simulate.py:70 ``FormationSimulator.step(input_velocity)``): vel [T, A, 2] is added to
+        the positions unscaled -> obs [T, A, D], rew [T, A], done [T, A]."""
+        if not isinstance(vel, torch.Tensor) or vel.dim() != 3:
+            raise AssertionError("velocities must be a [T, A, 2] tensor")
+        T = int(vel.shape[0])
+        v = self._check_vel(vel, (T,))
+        obs, rew, done = self._rollout_outputs(T, obs, rew, done, partial)
+        _lib.check(_lib.lib().fenv_rollout_velocity(
+            self._h, T, _lib.ptr(v), _lib.ptr(obs), _lib.ptr(rew), _lib.ptr(done),
+            _lib.ptr(partial), self._stream()), "fenv_rollout_velocity")
+        return obs, rew, done
+
+    def step_velocity_tensor(self, vel: torch.Tensor, obs=None, rew=None, done=None):
+        """One simulator step with raw velocities [A, 2] on device tensors; returns
+        (obs [A,D], rew [A], done [A] bool) like :meth:`step_tensor`."""
+        v = self._check_vel(vel, ())
+        obs = self.obs_dev if obs is None else obs
+        rew = self.rew_dev if rew is None else rew
+        done = self.done_dev if done is None else done
+        A, D = self.num_envs, self.obs_dim
+        self._check_out("obs", obs, (A, D), torch.float32)
+        self._check_out("rew", rew, (A,), torch.float32)
+        self._check_out("done", done, (A,), torch.bool)
+        _lib.check(_lib.lib().fenv_rollout_velocity(
+            self._h, 1, _lib.ptr(v), _lib.ptr(obs), _lib.ptr(rew), _lib.ptr(done), None,
+            self._stream()), "fenv_rollout_velocity")
+        return obs, rew, done
+
+    def step_velocity(self, vel):
+        """The numpy face of one velocity step: ``vel`` [A, 2] (numpy or tensor) ->
+        ``(obs, rewards, dones, infos)`` aliasing this env's host buffers, as :meth:`step`."""
+        host = self._ensure_host()
+        if isinstance(vel, torch.Tensor) and vel.is_cuda:
+            vel_p = _lib.ptr(self._check_vel(vel, ()))
+        else:
+            v = np.asarray(vel, dtype=np.float32)
+            if v.shape != (self.num_envs, 2):
+                raise AssertionError(f"velocities shape {v.shape} != {(self.num_envs, 2)}")
+            np.copyto(host.act, v)
+            vel_p = host.dev("act")
+        _lib.check(_lib.lib().fenv_rollout_velocity(
+            self._h, 1, vel_p, host.dev("obs"), host.dev("rew"), host.dev("done"), None,
+            self._stream()), "fenv_rollout_velocity")
+        self._host_result(host)
+        return host.obs, host.rew, host.done, self.infos
+
+    def rollout_control(self, T: int, vel_out=None, obs=None, rew=None, done=None, partial=None):
+        """T fused steps of the baseline controller (``fenv_rollout_control``): per step the
+        controller's velocities are computed in the kernel from the state held on chip and
+        applied.  ``vel_out`` [T, A, 2] (optional) receives them.  Identical to T times
+        :meth:`control_tensor` + :meth:`step_velocity_tensor`."""
+        T = int(T)
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        self._check_out("vel_out", vel_out, (T, self.num_envs, 2), torch.float32)
+        obs, rew, done = self._rollout_outputs(T, obs, rew, done, partial)
+        _lib.check(_lib.lib().fenv_rollout_control(
+            self._h, T, _lib.ptr(vel_out), _lib.ptr(obs), _lib.ptr(rew), _lib.ptr(done),
+            _lib.ptr(partial), self._stream()), "fenv_rollout_control")
         return obs, rew, done
 
     def policy_rollout(self, params: torch.Tensor, T: int, bufs: dict, seed: int = 0,
